@@ -133,7 +133,15 @@ def parse_args(argv=None):
                          "(tests compare the one-rank RCCL run with the plain run bit for bit)")
     ap.add_argument("--launch-test", action="store_true",
                     help="(CPU) exercise only the launcher: rendezvous over gloo, barrier, max-over-ranks, one JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: the "
+                         "reconstruction, warped image, offset field and losses, and after a training step the parameters and "
+                         "buffers of both networks; float32 / float64, at most 64 MB in all (a larger array is a fixed seeded "
+                         "sample of its flattened elements, <name>_sample.npy)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -276,6 +284,43 @@ def cpu_baseline(num_cascades, h, w, mode="train", coils=1, sparsity=0.25, batch
                       f"full warm-up step: " + "; ".join(f"N={lg['n']} on {lg['threads']} thread(s): {lg['steps']} step(s) in "
                                                           f"{lg['seconds']} s" for lg in legs) + f"; value = the best all-core leg (N={best['n']})",
             "legs": legs, "single_thread": one[0]["slices_per_s"] if one else None}
+
+
+DUMP_NAMES = ("img_rec", "img_warped", "img_offset", "loss_sim", "loss_smooth", "loss_all")
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(net):
+    """The output tensors a step leaves on the model (read from its __dict__: no deferred-input materialisation)."""
+    return {k: net.__dict__[k] for k in DUMP_NAMES if isinstance(net.__dict__.get(k), torch.Tensor)}
+
+
+def dump_outputs(path, outputs, net=None):
+    """Write ``outputs`` (name -> tensor) and, given ``net``, the flattened parameters + buffers of both networks as float32 /
+    float64 .npy files under ``path``.  The total stays within DUMP_BUDGET_BYTES: an array above its share is replaced by a
+    sample of its flattened elements at indices drawn by a fixed seed (the same indices for the same shape in every run)."""
+    import numpy as np
+    arrays = {}
+    for k, t in outputs.items():
+        t = t.detach()
+        if torch.is_complex(t):
+            t = torch.view_as_real(t)
+        arrays[k] = t if t.dtype == torch.float64 else t.float()
+    if net is not None:
+        for name, mod in (("params_R", net.net_R), ("params_T", net.net_T)):
+            ts = [p.detach().reshape(-1).float() for p in mod.parameters()] + \
+                 [b.detach().reshape(-1).float() for b in mod.buffers() if b.is_floating_point()]
+            arrays[name] = torch.cat(ts)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for k, t in arrays.items():
+        n = t.numel()
+        cap = share // t.element_size()
+        if n > cap:
+            idx = np.sort(np.random.default_rng(20260).choice(n, cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            k = k + "_sample"
+        np.save(os.path.join(path, k + ".npy"), t.cpu().numpy())
 
 
 def launch_test(args):
@@ -440,6 +485,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     graph = None
     timer = None
+    last_outputs = None                             # set when the last timed step is a recording whose outputs are not net's attributes
     step_mode = "eager"
     if args.mode == "train" and args.eager:
         net.auto_record = False                     # every timed step launched from Python
@@ -462,6 +508,7 @@ def main(argv=None):
                 timer = ops.KernelTimer(stride=10, strides={"fft_dc": 1, "fft_dc_bwd": 1}, alone=not args.brackets_as_shipped)
                 marked = net.record_update(img_full, img_aux, warmup=1, restore=False, timer=timer)
                 graph = marked
+                last_outputs = step_outputs(net)    # (the recording's own tensors: its replay refreshes them in place)
                 torch.cuda.synchronize()
                 plain_step, marked_replay, left = step, marked.replay, [args.steps]
 
@@ -471,6 +518,7 @@ def main(argv=None):
             except Exception as e:                  # pragma: no cover
                 print(f"[bench] the bracketed recording failed ({type(e).__name__}: {e}); no roofline figures", file=sys.stderr, flush=True)
                 timer = None
+                last_outputs = None
     if args.graph:
         # the arena, packed weights, twiddles and masks exist after warm-up, so the step neither
         # allocates through the library nor synchronises: it is capture-safe
@@ -515,6 +563,9 @@ def main(argv=None):
     ops.TIMER = None
     dt = sdist.max_over_ranks(dt, dist, dev)
     host_ms = 1e3 * sdist.max_over_ranks(host_s, dist, dev) / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs if last_outputs is not None else step_outputs(net),
+                     net if args.mode == "train" else None)
     allreduce_ms = exchange_detail = None
     if args.mode == "train" and dist is not None and not args.graph:
         # (a recorded step holds ONE set of event pairs, re-recorded by every replay: the last replay's duration)

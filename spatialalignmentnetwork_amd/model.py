@@ -460,7 +460,7 @@ class CSModel(BaseModel):
         replays).  ~2,500 launches per step then cost one graph launch on the host -- the form to use when eight ranks
         share one host.  The step count and (lr, weight decay, gradient scale) of both optimisers move to device
         memory (FusedAdamW.device_step / sync_hyper: change ``param_groups[0]['lr']``, call ``optim.sync_hyper()``, and
-        the next replay uses it); the weight gradients' side stream is captured as a fork / join.
+        the next replay uses it).
 
         Under a process group the step is recorded as two graphs -- forward + backward, optimiser -- with the gradient
         exchange issued eagerly between them; ``replay()`` hides the difference (``.mode`` says which form it is).
@@ -468,7 +468,25 @@ class CSModel(BaseModel):
 
         ``restore`` (default): parameters, AdamW moments, step counts and BatchNorm buffers are put back to their
         values from before the ``warmup`` real steps the capture needs (arena, packed weights, twiddles), so capturing
-        does not train on duplicated data."""
+        does not train on duplicated data.
+
+        The step is captured with its streams serialised: the weight gradients and the sensitivity branch run in line on the
+        capturing stream (ops.WGRAD_OVERLAP / SENS_OVERLAP off for the warm-up and the capture).  A replay of the captured
+        THREE-stream step crashed the process inside hipGraphLaunch (segmentation fault, first replay), and capturing and
+        replaying a graph of plain torch operations with the same stream pattern crashed as well (a side stream forked from the
+        main stream at every hand-off, its completion events waited on by the main stream hand-offs later, an auxiliary branch),
+        while captures of the one-stream inference pass replay fine: the fault is the runtime's, not this library's.  The serial
+        step is bit-identical to the overlapped one
+        (tests/test_gpu_step_runtime.py::test_overlapped_steps_equal_serial_steps_at_full_size); the recorded step
+        (record_update, the default replay form) keeps the overlap."""
+        saved = ops.WGRAD_OVERLAP[0], SENS_OVERLAP[0]
+        ops.WGRAD_OVERLAP[0] = SENS_OVERLAP[0] = False
+        try:
+            return self._capture_update(img_full, img_aux, warmup, restore)
+        finally:
+            ops.WGRAD_OVERLAP[0], SENS_OVERLAP[0] = saved
+
+    def _capture_update(self, img_full, img_aux, warmup: int, restore: bool):
         assert self.training is True
         dist = _active_dist()
         if dist is not None and not getattr(self, "_replicas_synced", False):

@@ -74,7 +74,7 @@ def test_training_steps_are_bit_reproducible_and_overlap_changes_nothing(S):
 
 # ------------------------------------------------------------------ hipGraph capture of the training step
 def test_captured_update_matches_eager(S):
-    """[round 2] CSModel.capture_update(): three replays of the captured 'Rec' step (two streams forked / joined inside the graph,
+    """[round 2] CSModel.capture_update(): three replays of the captured 'Rec' step (captured on one stream, against the overlapped eager steps;
     AdamW step count in device memory, weights re-packed by the captured batch launch) leave bit-identical parameters and
     BatchNorm buffers to three eager steps from the same state."""
     n, c, h, w = 2, 3, 48, 80
@@ -308,7 +308,7 @@ def test_recorded_forward_pass_replays_bit_identically(S):
 # ------------------------------------------------------------------------------------------- the reference's training loop
 @pytest.mark.parametrize("reg", ["Rec", "None"])
 def test_reference_train_loop_on_update_auto_records_bit_identically(S, reg):
-    """[round 4] /root/reference/train.py:212-217 verbatim: ``net.set_input(*batch); net.update()`` with a NEW batch every iteration.
+    """[round 4] The reference's train.py:212-217 verbatim: ``net.set_input(*batch); net.update()`` with a NEW batch every iteration.
     ``update()`` runs two steps eagerly, records the third (the recording does not advance the model) and replays from then
     on; a validation pass (``eval(); set_input; test(); train()``) in between, a learning-rate change and a change of the loss
     weight (which drops the recording) are followed.  Parameters, BatchNorm buffers, the reconstruction and the scalar losses
