@@ -378,7 +378,11 @@ int san_window_copy_fwd(const float* x, int x_ctot, int x_coff, const float* sc,
  * torch.cuda.amp.autocast, model.py:83-87,104).  parts = 3: operands split in three bf16 parts, six products per MAC,
  * fp32-equivalent (default, the only mode held to the 1e-4 parity bar); 2: two parts (16 mantissa bits), three
  * products; 1: plain bf16, one product.  Judged by PSNR against the parts = 3 output.  FFT, data consistency,
- * normalisation statistics and losses are fp32 in every mode.  Process-wide; returns SAN_E_ARG outside 1..3. */
+ * normalisation statistics and losses are fp32 in every mode.  parts = 17: the "fp16" mode -- ONE fp16 part per operand, one
+ * v_mfma_f32_16x16x32_f16 product per MAC (fp16's 11-bit significand at bf16's rate): weights packed with mode + 64 (one fp16
+ * part of w * S_w, the per-tensor power-of-two scale always on and written behind the image by the packing itself -- no caller
+ * initialisation), gradient inputs (data and weight gradients) scaled by the power of two of their amax record as in the
+ * two-part backward.  san_get_conv_precision returns 17 in that mode.  Process-wide; returns SAN_E_ARG for other values. */
 int san_set_conv_precision(int parts);
 int san_get_conv_precision(void);
 

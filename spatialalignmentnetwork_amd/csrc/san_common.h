@@ -27,7 +27,8 @@ struct SanGemm1x1Args {
     int N, H, W;
     int chunks, nblkp;
     int shuffle;               // 1: ConvTranspose2d 2x2 s2 -- 4 virtual channels per real channel + pixel shuffle
-    int bf1;                   // 1: bf16-format image, one part (plain bf16 operands, one product); 0: two fp16 parts, three products
+    int bf1;                   // 1: bf16-format image, one part (plain bf16 operands, one product); 0: two fp16 parts, three products;
+                               // 2: one fp16 part (the "fp16" mode, image packed with mode + 64), one product
     int slots;
     int ngrp, ptiles;          // (filled by the launcher)
 };
@@ -143,6 +144,10 @@ __device__ __forceinline__ void san_amax_record(unsigned* amax, int wg_linear, f
 }
 
 // bits of the tensor's largest magnitude (wave-uniform); every lane of the wave must be active
+// The one-part fp16 forms ("fp16" mode) stage forward activations without a scale: a magnitude beyond fp16's largest finite value
+// saturates to +-65504 instead of becoming inf (bf16, with fp32's exponent range, never overflows there).  NaN passes unchanged.
+__device__ __forceinline__ float san_sat_h(float v) { return __builtin_fabsf(v) > 65504.f ? __builtin_copysignf(65504.f, v) : v; }
+
 __device__ __forceinline__ uint32_t san_amax_read(const uint32_t* amax) {
     uint32_t b = amax[(threadIdx.x & 63) * SAN_AMAX_STRIDE];
 #pragma unroll

@@ -68,8 +68,12 @@ constexpr int kWD = 4;
 
 // BF1: the one-part plain-bf16 form of the narrow-precision modes (san_set_conv_precision(1): one product per MAC on part 0 of a
 // bf16-format image, activations rounded to bf16 while they are staged, no amax scale -- bf16 has fp32's exponent range).
-template <int NGW, bool SHUFFLE, bool BF1>
+// H1: the one-part fp16 form of the "fp16" mode (san_set_conv_precision(17)): one product per MAC on part 0 of an image packed with
+// mode + 64 (w S_w rounded to fp16 once), activations / gradient inputs (x S from the amax record) rounded to fp16 once.
+template <int NGW, bool SHUFFLE, bool BF1, bool H1 = false>
 __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a) {
+    static_assert(!(BF1 && H1), "one format");
+    constexpr bool ONE = BF1 || H1;                        // one operand part
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -125,7 +129,7 @@ __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a)
 #pragma unroll
             for (int m = 0; m < NGW; ++m) {
                 dst[m][0].u = src[(m * 4 * 3 + 0) * 64];
-                if constexpr (!BF1) dst[m][1].u = src[(m * 4 * 3 + 1) * 64];
+                if constexpr (!ONE) dst[m][1].u = src[(m * 4 * 3 + 1) * 64];
             }
         };
 #pragma unroll
@@ -161,12 +165,13 @@ __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a)
                             t0 = __builtin_amdgcn_fmed3f(t0, t0 * a.in_slope, lrelu_c);
                             t1 = __builtin_amdgcn_fmed3f(t1, t1 * a.in_slope, lrelu_c);
                             if constexpr (BF1) q1[i >> 1] = cvt_pk_b(t0, t1);
+                            else if constexpr (H1) q1[i >> 1] = cvt_pk_h(san_sat_h(t0), san_sat_h(t1));     // (saturated beyond 65504)
                             else split2h_pair(t0, t1, q1[i >> 1], q2[i >> 1]);
                         }
                     }
                     // (group `ngroups` = the zero columns behind the last K-step; pixels past the image are zero rows)
                     *reinterpret_cast<u32x4*>(lds1 + spx * S + g * 16) = u32x4{q1[0], q1[1], q1[2], q1[3]};
-                    if constexpr (!BF1) *reinterpret_cast<u32x4*>(lds2 + spx * S + g * 16) = u32x4{q2[0], q2[1], q2[2], q2[3]};
+                    if constexpr (!ONE) *reinterpret_cast<u32x4*>(lds2 + spx * S + g * 16) = u32x4{q2[0], q2[1], q2[2], q2[3]};
                 }
             }
         }
@@ -182,7 +187,7 @@ __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a)
 #pragma unroll
                     for (int b = 0; b < 4; ++b) {
                         x1[b].u = *reinterpret_cast<const u32x4*>(xrow + (size_t)(16 * b) * S + (c + d) * (kCKC * 2));
-                        if constexpr (!BF1) x2[b].u = *reinterpret_cast<const u32x4*>(xrow + (size_t)(16 * b) * S + (size_t)kTP * S + (c + d) * (kCKC * 2));
+                        if constexpr (!ONE) x2[b].u = *reinterpret_cast<const u32x4*>(xrow + (size_t)(16 * b) * S + (size_t)kTP * S + (c + d) * (kCKC * 2));
                     }
 #pragma unroll
                     for (int m = 0; m < NGW; ++m)
@@ -191,6 +196,9 @@ __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a)
                             if constexpr (BF1) {
                                 if constexpr (SHUFFLE) acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wq[d][m][0].v, x1[b].v, acc[m][b], 0, 0, 0);
                                 else acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[b].v, wq[d][m][0].v, acc[m][b], 0, 0, 0);
+                            } else if constexpr (H1) {
+                                if constexpr (SHUFFLE) acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[d][m][0].h, x1[b].h, acc[m][b], 0, 0, 0);
+                                else acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(x1[b].h, wq[d][m][0].h, acc[m][b], 0, 0, 0);
                             } else if constexpr (SHUFFLE) {       // D rows = channels: a lane ends with the 4 virtual channels of one real channel
                                 acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[d][m][0].h, x1[b].h, acc[m][b], 0, 0, 0);
                                 acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wq[d][m][0].h, x2[b].h, acc[m][b], 0, 0, 0);
@@ -371,22 +379,22 @@ __global__ void __launch_bounds__(kT) gemm1x1_f16_kernel(const SanGemm1x1Args a)
 // SAN_CONV1X1_GEMM=0 in the environment: off from the start (same-box A/B of whole steps)
 int g_gemm1x1 = (getenv("SAN_CONV1X1_GEMM") && atoi(getenv("SAN_CONV1X1_GEMM")) == 0) ? 0 : 1;
 
-template <int NGW, bool BF1>
+template <int NGW, bool BF1, bool H1 = false>
 int launch_ng(const SanGemm1x1Args& a, size_t lds, hipStream_t s) {
     const dim3 grid(a.ptiles * a.ngrp * a.N);
-    static SanPerDevice configured[2];
+    static SanPerDevice configured[2];           // (one set per instantiation: each template's function has its own attribute)
     const int k = a.shuffle ? 1 : 0;
     const int dev__ = san_current_device();
     if (!configured[k].has(dev__)) {
-        const void* fn = a.shuffle ? reinterpret_cast<const void*>(&gemm1x1_f16_kernel<NGW, true, BF1>) : reinterpret_cast<const void*>(&gemm1x1_f16_kernel<NGW, false, BF1>);
+        const void* fn = a.shuffle ? reinterpret_cast<const void*>(&gemm1x1_f16_kernel<NGW, true, BF1, H1>) : reinterpret_cast<const void*>(&gemm1x1_f16_kernel<NGW, false, BF1, H1>);
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
             san_set_error("cannot reserve 96 KB of LDS for the 1x1 GEMM");
             return SAN_E_UNSUPPORTED;
         }
         configured[k].mark(dev__);
     }
-    if (a.shuffle) hipLaunchKernelGGL((gemm1x1_f16_kernel<NGW, true, BF1>), grid, dim3(kT), lds, s, a);
-    else hipLaunchKernelGGL((gemm1x1_f16_kernel<NGW, false, BF1>), grid, dim3(kT), lds, s, a);
+    if (a.shuffle) hipLaunchKernelGGL((gemm1x1_f16_kernel<NGW, true, BF1, H1>), grid, dim3(kT), lds, s, a);
+    else hipLaunchKernelGGL((gemm1x1_f16_kernel<NGW, false, BF1, H1>), grid, dim3(kT), lds, s, a);
     return SAN_OK;
 }
 
@@ -421,7 +429,13 @@ int san_gemm1x1_f16_run(SanGemm1x1Args a, void* stream) {
     const size_t lds = (size_t)(a.bf1 ? 1 : 2) * kTP * pixel_stride(kc);
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (a.bf1) {
+    if (a.bf1 == 2) {
+        switch (NGW) {
+            case 1: rc = launch_ng<1, false, true>(a, lds, s); break;
+            case 2: rc = launch_ng<2, false, true>(a, lds, s); break;
+            default: rc = launch_ng<3, false, true>(a, lds, s); break;
+        }
+    } else if (a.bf1) {
         switch (NGW) {
             case 1: rc = launch_ng<1, true>(a, lds, s); break;
             case 2: rc = launch_ng<2, true>(a, lds, s); break;

@@ -107,7 +107,8 @@ struct BArgs {
     // with m = 2^32 / d + 1, exact while x d < 2^32 (checked by the host, which otherwise leaves m = 0 = "divide").
     // m_*: S, cgs, cgs * ntile, tiles_x, and for the run-time tile shapes hp, npx - 256, tw.
     unsigned m_S, m_cgs, m_cgsnt, m_tx, m_hp, m_rem, m_tw;
-    int fmt;                   // operand format of the packed weights / the staging: 0 = bf16 parts, 1 = two fp16 parts
+    int fmt;                   // operand format of the packed weights / the staging: 0 = bf16 parts, 1 = two fp16 parts, 2 = fp8,
+                               // 3 = ONE fp16 part (the "fp16" mode: image packed with mode + 64, always x S_w)
     unsigned long long* dbg;   // tuning hook (san_conv_bf16x3_debug_timeline): per workgroup 8 x u64 = 100 MHz clock at start, first
                                // chunk staged, epilogue start, end; HW_ID; XCC_ID -- null in normal use
     const uint32_t* amax;      // fp16 format on a GRADIENT input: the tensor's amax record (san_common.h); the input is scaled by a power of two
@@ -215,7 +216,7 @@ template <int MB, bool WD, int KS, bool FLAT, int NP, bool SWAP, bool F16, bool 
 __global__ void __launch_bounds__(kT, SAN_B16_MINWG(MB, WD, KS, NP)) conv_bf16x3_kernel(const BArgs a) {
     static_assert(NBW == 4 || (FLAT && KS == 3 && (NBW == 3 || NBW == 2)), "short tiles are a FLAT 3x3 form");
     constexpr int kU = NBW == 4 ? kUnits : 3;          // staging units per thread (short tiles: halo <= 256 pixels, no fourth slot)
-    static_assert(!F16 || NP == 2, "the fp16 format has two parts");
+    static_assert(!F16 || NP <= 2, "the fp16 format has two parts, or one (the \"fp16\" mode)");
     static_assert(!F8 || (NP == 1 && !F16), "the fp8 format has one part");
     constexpr int kSteps = KS == 3 ? 7 : 1;            // (shadows the 3x3 constant)
     static_assert(KS == 3 || WD, "the 1x1 form reads its weights directly");
@@ -467,6 +468,9 @@ __global__ void __launch_bounds__(kT, SAN_B16_MINWG(MB, WD, KS, NP)) conv_bf16x3
                 if constexpr (F8) {
                     vv[i] = v0;
                     vv[i + 1] = v1;
+                } else if constexpr (F16 && NP == 1) {         // one fp16 part: saturated, not inf, beyond 65504 (san_sat_h)
+                    q1[i >> 1] = cvt_pk_h(san_sat_h(v0), san_sat_h(v1));
+                    q2[i >> 1] = q3[i >> 1] = 0u;
                 } else if constexpr (F16) {
                     split2h_pair(v0, v1, q1[i >> 1], q2[i >> 1]);
                     q3[i >> 1] = 0u;
@@ -911,7 +915,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
 template <bool FULL>
 __device__ __forceinline__ void pack_unit(const float* __restrict__ w, uint16_t* __restrict__ packed, size_t u, int cout,
                                           int cin, int nblkp, int mode_, int ks, const float* __restrict__ wscale) {
-    const bool f16 = (mode_ & 16) != 0;            // mode + 16: two fp16 parts (parts 0, 1 of the image; part 2 zero)
+    const bool f16 = (mode_ & 80) != 0;            // mode + 16: two fp16 parts (parts 0, 1 of the image; part 2 zero); + 64: part 0 alone
     const bool f8 = (mode_ & 32) != 0;             // mode + 32: one fp8 e4m3 part x the tensor's scale (low 8 bytes of the part-0 slot)
     // fp8 AND (round 6, opt-in: san_conv_f16_wscale_enable) fp16 formats: the tensor's power-of-two scale S_w (exact), written behind
     // the image by the wscale pass ({1, 1} when off).  The fp16 parts then hold w S_w with max |w| S_w in [2^13, 2^14): the second
@@ -968,7 +972,7 @@ __device__ __forceinline__ void pack_unit(const float* __restrict__ w, uint16_t*
         q[0] = u32x4{cvt_f8x4(v8[0], v8[1], v8[2], v8[3]), cvt_f8x4(v8[4], v8[5], v8[6], v8[7]), 0u, 0u};
         q[1] = q[2] = u32x4{0u, 0u, 0u, 0u};
     }
-    const int parts = FULL ? 3 : (f8 ? 1 : (f16 ? 2 : 3));
+    const int parts = FULL ? 3 : ((f8 || (mode_ & 64)) ? 1 : (f16 ? 2 : 3));
 #pragma unroll
     for (int p = 0; p < 3; ++p)
         if (p < parts) *reinterpret_cast<u32x4*>(o + (size_t)p * 64 * 8) = q[p];
@@ -1035,7 +1039,7 @@ __global__ void __launch_bounds__(1024) fp8_wscale_kernel(const float* __restric
 __global__ void __launch_bounds__(1024) fp8_wscale_batch_kernel(const long long* __restrict__ jobs) {
     const long long* j = jobs + 8 * (size_t)blockIdx.x;
     const int m = (int)j[6];
-    if ((m & 32) == 0 && !((m & 16) && (m & 256))) return;      // fp8 images, and fp16 images that asked for a scale (bit 8)
+    if ((m & 96) == 0 && !((m & 16) && (m & 256))) return;      // fp8 and one-part fp16 images, and fp16 images that asked for a scale (bit 8)
     fp8_wscale(reinterpret_cast<const float*>(j[0]), (size_t)j[2] * (size_t)j[3] * (j[5] == 1 ? 1 : 9),
                reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(j[1]) + (size_t)j[7]), (m & 32) ? 7 : 13);
 }
@@ -1150,6 +1154,7 @@ int pick_mb_f16(int cin, int cout, int tiles) {
 }
 
 int g_conv_np = 3;             // operand parts of the bf16 convolutions / weight gradients (san_set_conv_precision)
+int g_conv_h1 = 0;             // 1: the one-part fp16 mode (san_set_conv_precision(17); g_conv_np is then 1)
 
 // Tile geometry of one 3x3 launch.  The default is tile_geom's (up to 256 pixels, four 16-pixel blocks per wave).  The SHORT form
 // (round 6, VERDICT r5 #1d: the 40^2 level leaves a third of the chip idle): full-width tiles of at most 192 pixels = three blocks per
@@ -1190,6 +1195,7 @@ std::unordered_map<const void*, int> g_fmt;
 void note_format(const void* packed, int mode) {
     std::lock_guard<std::mutex> lk(g_fmt_mu);
     if (mode & 32) g_fmt[packed] = 2;
+    else if (mode & 64) g_fmt[packed] = 3;
     else if (mode & 16) g_fmt[packed] = 1;
     else g_fmt.erase(packed);
 }
@@ -1236,6 +1242,10 @@ int launch_bf(const BArgs& a, hipStream_t s) {
         if (g_b16_swap && !a.shuffle && !FLAT) return launch_bfns<MB, WD, KS, FLAT, 2, true, true>(a, s);
         return launch_bfns<MB, WD, KS, FLAT, 2, false, true>(a, s);
     }
+    if (a.fmt == 3) {                               // one fp16 part (the "fp16" mode: forward and gradient operands)
+        if (g_b16_swap && !a.shuffle && !FLAT) return launch_bfns<MB, WD, KS, FLAT, 1, true, true>(a, s);
+        return launch_bfns<MB, WD, KS, FLAT, 1, false, true>(a, s);
+    }
     if (a.fmt == 2) {                               // one fp8 part (forward operands of the "fp8" mode)
         if (g_b16_swap && !a.shuffle && !FLAT) return launch_bfns<MB, WD, KS, FLAT, 1, true, false, true>(a, s);
         return launch_bfns<MB, WD, KS, FLAT, 1, false, false, true>(a, s);
@@ -1269,14 +1279,18 @@ int san_conv_f16_wscale_enable(int on) {
     return prev;
 }
 
+// parts = 17 (SAN_CONV_PRECISION_FP16): ONE fp16 part per operand, one v_mfma_f32_16x16x32_f16 product per MAC -- weight images
+// packed with mode + 64 (always x their power-of-two scale S_w, written by the library), gradient inputs x the power of two of
+// their amax record.  fp16's 11-bit significand at bf16's matrix rate.
 int san_set_conv_precision(int parts) {
-    SAN_CHECK_ARG(parts >= 1 && parts <= 3, "parts must be 1, 2 or 3");
-    g_conv_np = parts;
+    SAN_CHECK_ARG((parts >= 1 && parts <= 3) || parts == 17, "parts must be 1, 2, 3 or 17 (one fp16 part)");
+    g_conv_np = parts & 3;
+    g_conv_h1 = parts == 17 ? 1 : 0;
     san_wgrad_set_parts(parts);
     return SAN_OK;
 }
 
-int san_get_conv_precision(void) { return g_conv_np; }
+int san_get_conv_precision(void) { return g_conv_h1 ? 17 : g_conv_np; }
 
 // tuning / test hook: wd = -1 automatic, 0 LDS-staged weights, 1 weights-direct where MB <= 4; mb = -1 automatic or 2..5
 int san_conv_bf16x3_set_tuning(int wd, int mb) {
@@ -1337,11 +1351,11 @@ int san_conv3x3_bf16x3_stat_tiles(int n, int h, int w, int cin, int cout, int f1
 
 int san_conv_bf16x3_pack_ks(const float* w, void* packed, int cout, int cin, int mode, int ks, void* stream) {
     SAN_CHECK_ARG(w && packed, "null pointer");
-    SAN_CHECK_ARG(cout > 0 && cin > 0 && ((mode & 15) == 0 || (mode & 15) == 2) && (mode & ~48) == (mode & 15) && (mode & 48) != 48 && (ks == 1 || ks == 3), "bad dims / mode / ks");
+    SAN_CHECK_ARG(cout > 0 && cin > 0 && ((mode & 15) == 0 || (mode & 15) == 2) && (mode & ~112) == (mode & 15) && __builtin_popcount(mode & 112) <= 1 && (ks == 1 || ks == 3), "bad dims / mode / ks");
     // mode 2: `cout`, `cin` are those of the DATA-GRADIENT convolution (cout = forward cin, cin = forward cout)
     const BPlan p = bplan(cout, cin, ks);
     note_format(packed, mode);
-    if ((mode & 32) || ((mode & 16) && g_f16_wscale)) {
+    if ((mode & 96) || ((mode & 16) && g_f16_wscale)) {
         hipLaunchKernelGGL(fp8_wscale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, (size_t)cout * cin * (ks == 1 ? 1 : 9),
                            reinterpret_cast<float*>(static_cast<uint16_t*>(packed) + p.packed_elems), (mode & 32) ? 7 : 13);
         SAN_LAUNCH_CHECK();
@@ -1360,7 +1374,7 @@ int san_conv_bf16x3_pack(const float* w, void* packed, int cout, int cin, int mo
 
 int san_conv_bf16x3_pack_job_ks(long long* job8, const float* w, void* packed, int cout, int cin, int mode, int ks) {
     SAN_CHECK_ARG(job8 && w && packed, "null pointer");
-    SAN_CHECK_ARG(cout > 0 && cin > 0 && ((mode & 15) == 0 || (mode & 15) == 2) && (mode & ~48) == (mode & 15) && (mode & 48) != 48 && (ks == 1 || ks == 3), "bad dims / mode / ks");
+    SAN_CHECK_ARG(cout > 0 && cin > 0 && ((mode & 15) == 0 || (mode & 15) == 2) && (mode & ~112) == (mode & 15) && __builtin_popcount(mode & 112) <= 1 && (ks == 1 || ks == 3), "bad dims / mode / ks");
     const BPlan p = bplan(cout, cin, ks);
     note_format(packed, mode);
     job8[0] = (long long)(uintptr_t)w;
@@ -1414,15 +1428,20 @@ static int conv_bf16x3_run(const float* x, int x_ctot, int x_coff, int cin, cons
     a.fmt = format_of(w_packed);
     SAN_CHECK_ARG(a.fmt != 1 || g_conv_np == 3, "fp16-format weights are for the fp32-equivalent mode only");
     SAN_CHECK_ARG(a.fmt != 2 || g_conv_np == 1, "fp8-format weights are for the one-part mode only (san_set_conv_precision(1))");
-    a.amax = a.fmt == 1 ? static_cast<const uint32_t*>(amax) : nullptr;
+    SAN_CHECK_ARG(a.fmt != 3 || g_conv_h1, "one-part fp16 weights are for the fp16 mode only (san_set_conv_precision(17))");
+    a.amax = (a.fmt == 1 || a.fmt == 3) ? static_cast<const uint32_t*>(amax) : nullptr;
     a.f8_tail = a.fmt >= 1 ? reinterpret_cast<const float*>(static_cast<const uint16_t*>(w_packed) + p.packed_elems) : nullptr;     // {S_w, 1 / S_w}
     // the persistent form: two fp16 parts (fp32-equivalent mode) or one bf16 part (cout 18 / 36: the network's layers)
-    const bool stream_f16 = a.fmt == 1 && g_conv_np == 3, stream_bf1 = a.fmt == 0 && g_conv_np == 1 && (cout == 18 || cout == 36);
-    if (ks == 3 && (stream_f16 || stream_bf1) && !shuffle && g_b16_mb < 0 && g_b16_wd < 0 &&
+    // (and one fp16 part: every channel count the two-part form takes, the few-channel partial blocks included)
+    const bool stream_f16 = a.fmt == 1 && g_conv_np == 3, stream_bf1 = a.fmt == 0 && g_conv_np == 1 && !g_conv_h1 && (cout == 18 || cout == 36);
+    const bool stream_h1 = a.fmt == 3;
+    if (ks == 3 && (stream_f16 || stream_bf1 || stream_h1) && !shuffle && g_b16_mb < 0 && g_b16_wd < 0 &&
         san_conv_stream_eligible(n, h, w, cin, cout, x_ctot))
         return san_conv_stream_run(x, x_ctot, x_coff, cin, in_scale, in_shift, in_slope, w_packed, p.nblkp, bias, y, y_ctot, y_coff, cout,
-                                   part_stats, a.amax, n, h, w, stream, stream_f16 ? 2 : 1, stream_f16 ? a.f8_tail : nullptr);
-    if (ks == 1 && ((a.fmt == 1 && g_conv_np == 3) || (a.fmt == 0 && g_conv_np == 1)) && g_b16_mb < 0 && san_gemm1x1_enabled()) {
+                                   part_stats, a.amax, n, h, w, stream, stream_f16 ? 2 : (stream_h1 ? 17 : 1),
+                                   (stream_f16 || stream_h1) ? a.f8_tail : nullptr);
+    if (ks == 1 && ((a.fmt == 1 && g_conv_np == 3) || (a.fmt == 0 && g_conv_np == 1 && !g_conv_h1) || a.fmt == 3) && g_b16_mb < 0 &&
+        san_gemm1x1_enabled()) {
         // round 5: the whole K range staged once, no barrier between K-steps (san_conv1x1.hip)
         const TileGeom tg1 = tile_geom(h, w);
         SanGemm1x1Args g{};
@@ -1447,8 +1466,8 @@ static int conv_bf16x3_run(const float* x, int x_ctot, int x_coff, int cin, cons
         g.chunks = p.chunks;
         g.nblkp = p.nblkp;
         g.shuffle = shuffle;
-        g.bf1 = a.fmt == 0 ? 1 : 0;
-        g.w_tail = a.fmt == 1 ? a.f8_tail : nullptr;
+        g.bf1 = a.fmt == 0 ? 1 : (a.fmt == 3 ? 2 : 0);
+        g.w_tail = (a.fmt == 1 || a.fmt == 3) ? a.f8_tail : nullptr;
         g.slots = tg1.tiles_x * tg1.tiles_y * 4;
         return san_gemm1x1_f16_run(g, stream);
     }

@@ -111,8 +111,11 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // register allocation aims at
 // NPRT = 2: two fp16 parts per operand, three products per MAC (the fp32-equivalent mode); NPRT = 1: ONE bf16 part, one product
 // (san_set_conv_precision(1): BASELINE configs[1] as written; the packed image's leading bf16 part, activations rounded to bf16)
-template <int MBF, int REM, int OCC, int NPRT = 2>
+// H1 (NPRT = 1 only): ONE fp16 part instead -- the "fp16" mode (san_set_conv_precision(17)): part 0 of an image packed with mode + 64
+// (w S_w rounded to fp16 once), activations / gradient inputs (x S) rounded to fp16 once, one v_mfma_f32_16x16x32_f16 per MAC
+template <int MBF, int REM, int OCC, int NPRT = 2, bool H1 = false>
 __global__ void __launch_bounds__(kT, OCC) conv3x3_stream_kernel(const SArgs a) {
+    static_assert(!H1 || NPRT == 1, "the fp16 form of one part");
     constexpr int MB = MBF + (REM > 0 ? 1 : 0);
     constexpr int RS = MBF * 1024 + (REM > 0 ? REM * 64 + 16 : 0);      // LDS bytes of one (step, part) weight region
     constexpr int RSL = RS / 16;                                        // ... in 16-byte slots
@@ -248,7 +251,7 @@ __global__ void __launch_bounds__(kT, OCC) conv3x3_stream_kernel(const SArgs a) 
             inInvS = __builtin_bit_cast(float, (uint32_t)(e - 13) << 23);
         }
     }
-    if (NPRT == 2 && a.w_tail) inInvS *= a.w_tail[1];    // fp16-format weights may be stored x S_w (round 6): exact power of two
+    if ((NPRT == 2 || H1) && a.w_tail) inInvS *= a.w_tail[1];    // fp16-format weights may be stored x S_w (round 6): exact power of two
     // lazy-affine table of image n: [chunk][scale 24 | shift 24]
     auto load_aff = [&](int n_) {
         if (tid < a.chunks * 48) {
@@ -314,6 +317,8 @@ __global__ void __launch_bounds__(kT, OCC) conv3x3_stream_kernel(const SArgs a) 
                         const float v1 = __builtin_amdgcn_fmed3f(a1, a1 * a.in_slope, lrelu_c);
                         if constexpr (NPRT == 2)
                             split2h_pair(v0, v1, q1[i >> 1], q2[i >> 1]);
+                        else if constexpr (H1)
+                            q1[i >> 1] = cvt_pk_h(san_sat_h(v0), san_sat_h(v1));      // (saturated, not inf, beyond 65504)
                         else
                             q1[i >> 1] = cvt_pk_bf(v0, v1);
                     }
@@ -384,8 +389,10 @@ __global__ void __launch_bounds__(kT, OCC) conv3x3_stream_kernel(const SArgs a) 
 #pragma unroll
                     for (int m = 0; m < MB; ++m)
 #pragma unroll
-                        for (int b = 0; b < 4; ++b)
-                            acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[s & 1][b][0].v, wa[s & 1][m][0].v, acc[m][b], 0, 0, 0);
+                        for (int b = 0; b < 4; ++b) {
+                            if constexpr (H1) acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xa[s & 1][b][0].h, wa[s & 1][m][0].h, acc[m][b], 0, 0, 0);
+                            else acc[m][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[s & 1][b][0].v, wa[s & 1][m][0].v, acc[m][b], 0, 0, 0);
+                        }
                 } else {
                     // (x hi, w hi | mixed), (x lo, w hi), (x hi, w lo of the full blocks)
 #pragma unroll
@@ -505,14 +512,14 @@ size_t stream_lds_bytes(int cin, int cout, int nprt = 2) {
     return 2 * (size_t)kPartB + (size_t)chunks * 192 + (size_t)kSteps * nprt * rs;     // operand image, affine table, one chunk of weights
 }
 
-template <int MBF, int REM, int OCC, int NPRT = 2>
+template <int MBF, int REM, int OCC, int NPRT = 2, bool H1 = false>
 int launch_stream(const SArgs& a, hipStream_t s) {
     const size_t lds = stream_lds_bytes(a.cin, a.cout, NPRT);
     static size_t configured_on[128] = {};      // per device: the attribute is a per-device setting (round 6)
     const int dev__ = san_current_device();
     size_t& configured = configured_on[dev__ >= 0 && dev__ < 128 ? dev__ : 0];
     if (lds > configured || dev__ < 0 || dev__ >= 128) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel<MBF, REM, OCC, NPRT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_stream_kernel<MBF, REM, OCC, NPRT, H1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess) {
             san_set_error("cannot reserve %d bytes of LDS for the stream convolution", (int)lds);
             return SAN_E_UNSUPPORTED;
@@ -525,7 +532,7 @@ int launch_stream(const SArgs& a, hipStream_t s) {
     int grid = 256 * per_cu;
     const int need = ((a.total + 7) / 8) * 8;           // (a multiple of 8: the tile ranges are per XCD)
     if (grid > need) grid = need;
-    hipLaunchKernelGGL((conv3x3_stream_kernel<MBF, REM, OCC, NPRT>), dim3(grid), dim3(kT), lds, s, a);
+    hipLaunchKernelGGL((conv3x3_stream_kernel<MBF, REM, OCC, NPRT, H1>), dim3(grid), dim3(kT), lds, s, a);
     return SAN_OK;
 }
 
@@ -595,7 +602,18 @@ int san_conv_stream_run(const float* x, int x_ctot, int x_coff, int cin, const f
     SAN_CHECK_ARG((reinterpret_cast<uintptr_t>(y) & 15) == 0, "stream convolution: output must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    if (nprt == 1) {                                    // one bf16 part (the layers of the network only)
+    if (nprt == 17) {                                   // one fp16 part: every channel count of the two-part form
+        switch (cout) {
+            case 2: rc = launch_stream<0, 2, 2, 1, true>(a, s); break;
+            case 3: rc = launch_stream<0, 3, 2, 1, true>(a, s); break;
+            case 16: rc = launch_stream<1, 0, 2, 1, true>(a, s); break;
+            case 18: rc = launch_stream<1, 2, 2, 1, true>(a, s); break;
+            case 32: rc = launch_stream<2, 0, 2, 1, true>(a, s); break;
+            case 36: rc = launch_stream<2, 4, 2, 1, true>(a, s); break;
+            case 48: rc = launch_stream<3, 0, 2, 1, true>(a, s); break;
+            default: san_set_error("stream convolution: unsupported cout %d", cout); return SAN_E_UNSUPPORTED;
+        }
+    } else if (nprt == 1) {                             // one bf16 part (the layers of the network only)
         switch (cout) {
             case 18: rc = launch_stream<1, 2, 2, 1>(a, s); break;
             case 36: rc = launch_stream<2, 4, 2, 1>(a, s); break;

@@ -68,8 +68,13 @@ __device__ __forceinline__ uint32_t cvt_pk_h(float a, float b) {
     fl2 v = {a, b};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, hf2));
 }
-template <bool F16>
+// SAT: saturate at fp16's largest finite value first (the activation operand of the one-part fp16 forms, san_sat_h)
+template <bool F16, bool SAT = false>
 __device__ __forceinline__ void split_pair(float f0, float f1, uint32_t& p1, uint32_t& p2, uint32_t& p3) {
+    if constexpr (SAT) {
+        f0 = san_sat_h(f0);
+        f1 = san_sat_h(f1);
+    }
     if constexpr (F16) {
         p1 = cvt_pk_h(f0, f1);
         const hf2 h = __builtin_bit_cast(hf2, p1);
@@ -360,7 +365,7 @@ struct WDArgs {
 // NP: operand parts used (3 = fp32-equivalent, six products; 2 = three products; 1 = plain bf16), san_set_conv_precision
 template <int NB, int NP, bool F16>
 __global__ void __launch_bounds__(kWT) wgrad_bf16x3_direct_kernel(const WDArgs a) {
-    static_assert(!F16 || NP == 2, "the fp16 form has two parts");
+    static_assert(!F16 || NP <= 2, "the fp16 form has two parts, or one (the \"fp16\" mode)");
     float dyS, dyInvS;
     amax_scale(F16 ? a.amax : nullptr, dyS, dyInvS);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -430,9 +435,9 @@ __global__ void __launch_bounds__(kWT) wgrad_bf16x3_direct_kernel(const WDArgs a
         const float vr = (ok && right_ok) ? san_act(xr_, sc, sh, slope) : 0.f;
         uint32_t d[3][4], dm[3], dp[3];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) split_pair<F16>(v[2 * i], v[2 * i + 1], d[0][i], d[1][i], d[2][i]);
-        split_pair<F16>(0.f, vl, dm[0], dm[1], dm[2]);       // high half = the pixel to the left
-        split_pair<F16>(vr, 0.f, dp[0], dp[1], dp[2]);       // low half = the pixel to the right
+        for (int i = 0; i < 4; ++i) split_pair<F16, F16 && NP == 1>(v[2 * i], v[2 * i + 1], d[0][i], d[1][i], d[2][i]);
+        split_pair<F16, F16 && NP == 1>(0.f, vl, dm[0], dm[1], dm[2]);       // high half = the pixel to the left
+        split_pair<F16, F16 && NP == 1>(vr, 0.f, dp[0], dp[1], dp[2]);       // low half = the pixel to the right
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
             const uint32_t s01 = __builtin_amdgcn_alignbit(d[p][1], d[p][0], 16), s12 = __builtin_amdgcn_alignbit(d[p][2], d[p][1], 16),
@@ -571,7 +576,7 @@ struct W1Args {
 
 template <int NB, int NP, bool F16>
 __global__ void __launch_bounds__(kWT) wgrad1x1_bf16x3_kernel(const W1Args a) {
-    static_assert(!F16 || NP == 2, "the fp16 form has two parts");
+    static_assert(!F16 || NP <= 2, "the fp16 form has two parts, or one (the \"fp16\" mode)");
     float dyS, dyInvS;
     amax_scale(F16 ? a.amax : nullptr, dyS, dyInvS);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -627,9 +632,9 @@ __global__ void __launch_bounds__(kWT) wgrad1x1_bf16x3_kernel(const W1Args a) {
         uint32_t d[3][4];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            split_pair<F16>(ok ? san_act(xlo[2 * i], sc, sh, slope) : 0.f, ok ? san_act(xlo[2 * i + 1], sc, sh, slope) : 0.f, d[0][i], d[1][i],
+            split_pair<F16, F16 && NP == 1>(ok ? san_act(xlo[2 * i], sc, sh, slope) : 0.f, ok ? san_act(xlo[2 * i + 1], sc, sh, slope) : 0.f, d[0][i], d[1][i],
                         d[2][i]);
-            split_pair<F16>(okh ? san_act(xhi[2 * i], sc, sh, slope) : 0.f, okh ? san_act(xhi[2 * i + 1], sc, sh, slope) : 0.f, d[0][2 + i],
+            split_pair<F16, F16 && NP == 1>(okh ? san_act(xhi[2 * i], sc, sh, slope) : 0.f, okh ? san_act(xhi[2 * i + 1], sc, sh, slope) : 0.f, d[0][2 + i],
                         d[1][2 + i], d[2][2 + i]);
         }
 #pragma unroll
@@ -849,6 +854,7 @@ int launch_wb(const WBArgs& a, int grid, hipStream_t s) {
 }
 
 int g_wgrad_np = 3;            // operand parts (san_set_conv_precision)
+int g_wgrad_h1 = 0;            // 1: the "fp16" mode -- with an amax record, ONE fp16 part per operand (one product per MAC)
 
 template <int NB, int NP, bool F16 = false>
 int launch_wdn(const WDArgs& a, int grid, hipStream_t s) {
@@ -870,6 +876,7 @@ int launch_wdn(const WDArgs& a, int grid, hipStream_t s) {
 template <int NB>
 int launch_wd(const WDArgs& a, int grid, hipStream_t s) {
     if (a.amax && g_wgrad_np == 3) return launch_wdn<NB, 2, true>(a, grid, s);      // two fp16 parts, dy scaled by its maximum
+    if (a.amax && g_wgrad_h1) return launch_wdn<NB, 1, true>(a, grid, s);           // one fp16 part, dy scaled by its maximum
     switch (g_wgrad_np) {
         case 1: return launch_wdn<NB, 1>(a, grid, s);
         case 2: return launch_wdn<NB, 2>(a, grid, s);
@@ -943,6 +950,10 @@ int launch_w1(const W1Args& a, int grid, hipStream_t s) {
         hipLaunchKernelGGL((wgrad1x1_bf16x3_kernel<NB, 2, true>), dim3(grid), dim3(kWT), lds, s, a);
         return SAN_OK;
     }
+    if (a.amax && g_wgrad_h1) {
+        hipLaunchKernelGGL((wgrad1x1_bf16x3_kernel<NB, 1, true>), dim3(grid), dim3(kWT), lds, s, a);
+        return SAN_OK;
+    }
     switch (g_wgrad_np) {
         case 1: hipLaunchKernelGGL((wgrad1x1_bf16x3_kernel<NB, 1, false>), dim3(grid), dim3(kWT), lds, s, a); break;
         case 2: hipLaunchKernelGGL((wgrad1x1_bf16x3_kernel<NB, 2, false>), dim3(grid), dim3(kWT), lds, s, a); break;
@@ -964,7 +975,11 @@ bool wb_direct(const float* x, const float* dy, int n, int h, int w, int x_ctot,
 }  // namespace
 
 // the split-plane form (rows that are not 16-byte aligned) always runs with three parts
-void san_wgrad_set_parts(int parts) { g_wgrad_np = parts; }
+// (parts = 17: the one-part fp16 mode, see san_set_conv_precision)
+void san_wgrad_set_parts(int parts) {
+    g_wgrad_np = parts & 3;
+    g_wgrad_h1 = parts == 17 ? 1 : 0;
+}
 
 extern "C" {
 

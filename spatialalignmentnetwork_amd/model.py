@@ -104,10 +104,15 @@ class CSModel(BaseModel):
         self.use_amp = bool(get("use_amp", False))
         # The reference's mixed-precision seam is torch.cuda.amp.autocast(enabled=use_amp) around the forwards
         # (model.py:83-87,104).  Here it selects the arithmetic of the matrix-core convolutions: cfg.conv_dtype in
-        # {"bf16x3" (fp32-equivalent, default), "bf16x2", "bf16", "fp8" (e4m3 forward, bf16 gradients)}; use_amp without conv_dtype means plain bf16.  FFT, data
+        # {"bf16x3" (fp32-equivalent, default), "bf16x2", "bf16", "fp8" (e4m3 forward, bf16 gradients), "fp16" (one fp16 part per
+        # operand: forward, data and weight gradients)}; use_amp without conv_dtype means plain bf16.  FFT, data
         # consistency, normalisation statistics and losses are fp32 in every mode; no GradScaler is needed (bf16 has
         # fp32's exponent range).
         self.conv_dtype = get("conv_dtype", None)      # None: follow use_amp (which eval.py:41 switches off after loading)
+        # SAN_CONV_DTYPE (environment): the mode use_amp selects when the config has no conv_dtype key -- "bf16" when unset.  The
+        # reference's unmodified train.py gets fp16 operands for --use_amp through dropin/ this way (SAN_CONV_DTYPE=fp16), and its
+        # eval.py, which switches use_amp off after loading, still evaluates in the fp32-equivalent mode as the reference does.
+        self.amp_dtype = os.environ.get("SAN_CONV_DTYPE") or "bf16"
         # cfg.bwd_dtype (optional): arithmetic of the BACKWARD convolutions (data and weight gradients) only, e.g. "bf16x2"
         # under an fp32-equivalent forward: the outputs keep the 1e-4 parity, the gradients carry 16 mantissa bits
         # (4e-6 per layer, against the 1e-2-level fp32-vs-fp64 noise of the reference's own gradients).  Default: as forward.
@@ -116,6 +121,8 @@ class CSModel(BaseModel):
             raise ValueError(f"cfg.bwd_dtype {self.bwd_dtype!r}: choose from {sorted(ops.CONV_PRECISIONS)}")
         if self.conv_dtype is not None and self.conv_dtype not in ops.CONV_PRECISIONS:
             raise ValueError(f"cfg.conv_dtype {self.conv_dtype!r}: choose from {sorted(ops.CONV_PRECISIONS)}")
+        if self.amp_dtype not in ops.CONV_PRECISIONS:
+            raise ValueError(f"SAN_CONV_DTYPE {self.amp_dtype!r}: choose from {sorted(ops.CONV_PRECISIONS)}")
         self.device = torch.device("cpu")
 
     # ------------------------------------------------------------------ inputs
@@ -332,7 +339,7 @@ class CSModel(BaseModel):
                dist.get_world_size() if dist is not None else 1, self.net_T.training, self.net_R.training,
                tuple(p.requires_grad for o in (self.optim_R, self.optim_T) for p in o._params()),
                tuple(o.bucket().flat_p.data_ptr() for o in (self.optim_R, self.optim_T)), pr.data_ptr(), pr._version,
-               ops.F16_FWD[0], ops.F16_BWD[0], ops.USE_BF16X3[0], ops.WGRAD_OVERLAP[0], ops.WGRAD_DEFER[0], SENS_OVERLAP[0],
+               ops.F16_FWD[0], ops.F16_BWD[0], ops.F16_WSCALE[0], ops.USE_BF16X3[0], ops.WGRAD_OVERLAP[0], ops.WGRAD_DEFER[0], SENS_OVERLAP[0],
                bool(getattr(self, "time_exchange", False)), os.environ.get("SAN_GRAD_EXCHANGE", "allreduce"),
                # baked into the recording as host-side arguments: the low-frequency count of the sensitivity estimate, AdamW's
                # betas / eps (lr, weight decay and the step count live in device memory: sync_hyper)
@@ -373,7 +380,7 @@ class CSModel(BaseModel):
         self.step_mode = "replay of a recorded step (auto-recorded by update())"
 
     def _conv_mode(self) -> str:
-        return self.conv_dtype or ("bf16" if self.use_amp else "bf16x3")
+        return self.conv_dtype or (self.amp_dtype if self.use_amp else "bf16x3")
 
     def _update(self, part: str = "all"):
         """One optimisation step.  Regimes 'None' (train R, T frozen) and 'Rec' (train T and R through

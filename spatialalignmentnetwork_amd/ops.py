@@ -141,7 +141,7 @@ def _timed(name, work, unit, fn, abytes=0.0, products=0):
 
 
 def _products(f16: bool = False) -> int:
-    return 3 if (f16 and _CONV_NP[0] == 3) else {3: 6, 2: 3, 1: 1}[_CONV_NP[0]]
+    return 3 if (f16 and _CONV_NP[0] == 3) else {3: 6, 2: 3, 1: 1}[_CONV_NP[0]]      # (the "fp16" mode: NP 1, one product)
 
 
 def _conv_abytes(n, h, w, cin, cout, ks):
@@ -762,7 +762,7 @@ class _PackRegistryBf16(_PackRegistry):
             return self._alloc_zeroed(w, mode)
 
     def _alloc_zeroed(self, w: torch.Tensor, mode: int):
-        mode &= 15                                      # (+16 = two fp16 parts, +32 = one fp8 part instead of bf16 parts: same image size)
+        mode &= 15                                      # (+16 = two fp16 parts, +32 = one fp8 part, +64 = one fp16 part: same image size)
         if mode == 3:                                   # ConvTranspose2d [Cin, Cout, 2, 2] as a 1x1 conv to 4 Cout channels
             return (4 * w.shape[1], w.shape[0], 1), _scale_tail_one(torch.zeros(
                 lib().query("san_conv_bf16x3_packed_bytes_ks", 4 * w.shape[1], w.shape[0], 1), device=w.device, dtype=torch.uint8))
@@ -781,8 +781,9 @@ class _PackRegistryBf16(_PackRegistry):
 
     @staticmethod
     def _cmode(mode: int) -> int:
-        """registry mode -> library mode: 3 (transposed) packs like a data gradient (2); bits 4 (fp16 parts) / 5 (fp8) pass through"""
-        return (2 if (mode & 15) == 3 else (mode & 15)) | (mode & 48)
+        """registry mode -> library mode: 3 (transposed) packs like a data gradient (2); bits 4 (fp16 parts) / 5 (fp8) / 6 (one
+        fp16 part) pass through"""
+        return (2 if (mode & 15) == 3 else (mode & 15)) | (mode & 112)
 
     @staticmethod
     def _blocks(j) -> int:
@@ -804,7 +805,7 @@ class _PackRegistryBf16(_PackRegistry):
         if stale:
             self.classes = []                       # (first job, count, workgroups per job, any fp8 image)
             for i, j in enumerate(self.order):
-                b, f8 = self._blocks(j), 1 if ((j["mode"] & 32) or ((j["mode"] & 16) and F16_WSCALE[0])) else 0     # (images with a per-tensor scale: the wscale pass)
+                b, f8 = self._blocks(j), 1 if ((j["mode"] & 96) or ((j["mode"] & 16) and F16_WSCALE[0])) else 0     # (images with a per-tensor scale: the wscale pass)
                 if self.classes and self.classes[-1][2] == b:
                     first, cnt, _, f = self.classes[-1]
                     self.classes[-1] = (first, cnt + 1, b, f | f8)
@@ -832,12 +833,26 @@ _CONV_NP = [3]
 # "fp8" mode (BASELINE config 5): FORWARD convolutions on one OCP e4m3 part per operand (per-tensor power-of-two weight scale,
 # activations x 8: csrc/san_conv_bf16.hip "fp8"); data and weight gradients on plain bf16; FFT / DC / norms / losses fp32.
 _FP8_FWD = [False]
+# "fp16" mode: ONE fp16 part per operand (one product per MAC) for the forward, data-gradient and weight-gradient convolutions:
+# weight images packed with mode + 64 (w S_w, the per-tensor power-of-two scale always on), gradient inputs scaled by the power of
+# two of their amax record (csrc/san_conv_bf16.hip, san_set_conv_precision(17))
+_F16_ONE = [False]
 
 
 def _fwd_fmt() -> int:
+    if _F16_ONE[0]:
+        return 64
     if _FP8_FWD[0] and _CONV_NP[0] == 1:
         return 32
     return 16 if (F16_FWD[0] and _CONV_NP[0] == 3) else 0
+
+
+def _grad_fmt() -> int:
+    """Image format of the data-gradient convolutions whose input carries an amax record: one fp16 part ("fp16" mode), two fp16
+    parts (fp32-equivalent mode), or 0 (bf16 parts, no amax scale)."""
+    if _F16_ONE[0]:
+        return 64
+    return 16 if _CONV_NP[0] == 3 else 0
 
 
 # Gradients on two fp16 parts need a per-tensor power-of-two scale: the kernels that WRITE a dy tensor (san_act_bwd*_amax)
@@ -873,7 +888,7 @@ class AmaxPool:
         self.idx = 0
 
     def next(self, device) -> Optional[torch.Tensor]:
-        if not (F16_BWD[0] and _CONV_NP[0] == 3):
+        if not ((F16_BWD[0] and _CONV_NP[0] == 3) or _F16_ONE[0]):
             return None
         key = _dev_key(device)
         t = self.buf.get(key)
@@ -913,22 +928,27 @@ AMAX = AmaxPool()
 
 # Arithmetic of the matrix-core convolutions / weight gradients (san_set_conv_precision).  "bf16x3" is the default and the
 # only mode held to the 1e-4 parity bar; "bf16x2" / "bf16" are the narrow-precision modes (PSNR-judged).
-CONV_PRECISIONS = {"bf16x3": 3, "fp32": 3, "bf16x2": 2, "bf16": 1, "fp8": 1}
+# "fp16": one fp16 part per operand (san_set_conv_precision(17)), forward and both gradients.
+CONV_PRECISIONS = {"bf16x3": 3, "fp32": 3, "bf16x2": 2, "bf16": 1, "fp8": 1, "fp16": 1}
+_C_FP16 = 17                    # san_set_conv_precision's code of the "fp16" mode
 
 
 def set_conv_precision(mode: str) -> str:
     """Select the operand parts of every bf16 matrix-core kernel (process-wide); returns the previous mode's name."""
     if mode not in CONV_PRECISIONS:
         raise ValueError(f"conv precision {mode!r}: choose from {sorted(CONV_PRECISIONS)}")
-    prev = {3: "bf16x3", 2: "bf16x2", 1: "fp8" if _FP8_FWD[0] else "bf16"}[lib().query("san_get_conv_precision")]
-    lib().call("san_set_conv_precision", CONV_PRECISIONS[mode])
+    prev = {3: "bf16x3", 2: "bf16x2", 1: "fp8" if _FP8_FWD[0] else "bf16", _C_FP16: "fp16"}[lib().query("san_get_conv_precision")]
+    lib().call("san_set_conv_precision", _C_FP16 if mode == "fp16" else CONV_PRECISIONS[mode])
     _CONV_NP[0] = CONV_PRECISIONS[mode]
     _FP8_FWD[0] = mode == "fp8"
+    _F16_ONE[0] = mode == "fp16"
     return prev
 
 
 def current_precision() -> str:
     """The mode set_conv_precision last selected."""
+    if _F16_ONE[0]:
+        return "fp16"
     return {3: "bf16x3", 2: "bf16x2", 1: "fp8" if _FP8_FWD[0] else "bf16"}[_CONV_NP[0]]
 
 
@@ -1022,11 +1042,11 @@ def conv2d(x: Act, weight: torch.Tensor, bias: Optional[torch.Tensor], y: Act, s
     # (round 6) a 3x3 convolution TO 2 / 3 channels (the alignment net's last layer, unet.py:108-111) on the persistent matrix-core
     # kernel with those channels as a partial block alone, where its shape rules hold -- the one-tile kernel does not take such a layer
     small = (STREAM_SMALL_COUT[0] and ks == 3 and cout in (2, 3) and cin >= 16 and out_scale is None and not stats and not grad_input
-             and USE_BF16X3[0] and _fwd_fmt() == 16 and y.buf.data_ptr() % 16 == 0
+             and USE_BF16X3[0] and _fwd_fmt() in (16, 64) and y.buf.data_ptr() % 16 == 0
              and lib().query("san_conv_stream_eligible", n, h, w, cin, cout, x.ctot))
     if out_scale is None and (small or bf16x3_eligible(cin, cout, h, w, ks)):
         # bf16 matrix cores, operands split in three (fp32-level accuracy), csrc/san_conv_bf16.hip
-        fmt = (16 if (x.amax is not None and _CONV_NP[0] == 3) else 0) if grad_input else _fwd_fmt()
+        fmt = (_grad_fmt() if x.amax is not None else 0) if grad_input else _fwd_fmt()
         wp = PACKS16.get(weight, fmt)
         if grad_input and fmt:
             # a gradient through a plain convolution (the transposed convolution's data gradient): fp16 parts, scaled by its maximum
@@ -1291,12 +1311,13 @@ def conv2d_dgrad(dy: Act, weight: torch.Tensor, dx: Act) -> None:
     """dx.buf[:, dx.coff:+cin] = dL/d(conv input) for dy = dL/d(conv output) (materialised)."""
     cout, cin, ks = weight.shape[0], weight.shape[1], weight.shape[2]
     assert dy.c == cout and dx.c == cin
-    small = (STREAM_SMALL_COUT[0] and ks == 3 and cin in (2, 3) and cout >= 16 and USE_BF16X3[0] and dy.amax is not None and _CONV_NP[0] == 3
+    gfmt = _grad_fmt()
+    small = (STREAM_SMALL_COUT[0] and ks == 3 and cin in (2, 3) and cout >= 16 and USE_BF16X3[0] and dy.amax is not None and gfmt
              and dy.scale is None and dx.buf.data_ptr() % 16 == 0
              and lib().query("san_conv_stream_eligible", dy.n, dy.h, dy.w, cout, cin, dy.ctot))
     if small or bf16x3_eligible(cout, cin, dy.h, dy.w, ks):       # the data-gradient conv maps cout -> cin channels
-        if dy.amax is not None and _CONV_NP[0] == 3 and dy.scale is None:
-            wp = PACKS16.get(weight, 2 + 16)             # two fp16 parts; dy scaled by the power of two its maximum asks for
+        if dy.amax is not None and gfmt and dy.scale is None:
+            wp = PACKS16.get(weight, 2 + gfmt)           # fp16 part(s); dy scaled by the power of two its maximum asks for
             nbytes = lib().query("san_conv_bf16x3_ws_bytes", dy.n, dy.h, dy.w, cout, cin, 3) if ks == 3 else 0
             ws = GLOBAL_ARENA.scratch("b16_splitk", nbytes, dy.buf.device) if nbytes else None
             gargs = (_p(dy.buf), dy.ctot, dy.coff, cout, _p(wp), _p(dx.buf), dx.ctot, dx.coff, cin, _p(dy.amax), dy.n, dy.h, dy.w,
@@ -1550,15 +1571,15 @@ def _on_side_stream(dy: Act, x: Act, fn) -> None:
         fn(x, dy)
         return
     dy, x = dataclasses.replace(dy), dataclasses.replace(x)
-    mode = _CONV_NP[0], _FP8_FWD[0]
+    mode = _CONV_NP[0], _FP8_FWD[0], _F16_ONE[0]
 
     def launch(fn=fn, x=x, dy=dy, mode=mode):
-        saved = _CONV_NP[0], _FP8_FWD[0]
-        _CONV_NP[0], _FP8_FWD[0] = mode
+        saved = _CONV_NP[0], _FP8_FWD[0], _F16_ONE[0]
+        _CONV_NP[0], _FP8_FWD[0], _F16_ONE[0] = mode
         try:
             fn(x, dy)
         finally:
-            _CONV_NP[0], _FP8_FWD[0] = saved
+            _CONV_NP[0], _FP8_FWD[0], _F16_ONE[0] = saved
 
     _WG["pending"].append((dy, x, launch))
     _WG["pending_ptrs"].add(dy.buf.data_ptr())
@@ -1645,7 +1666,7 @@ def _conv2d_wgrad_bf16x3(x: Act, dy: Act, dw: torch.Tensor, accumulate: bool = F
     nbytes = lib().query("san_conv_wgrad_bf16x3_scratch_bytes", x.n, x.h, x.w, cin, cout)
     scratch_tag, restore = _wgrad_scratch_tag(dw, scratch_tag)
     scratch = arena.scratch("wgrad_bf16x3" + scratch_tag, nbytes, x.buf.device)
-    f16 = dy.amax is not None and _CONV_NP[0] == 3
+    f16 = dy.amax is not None and (_CONV_NP[0] == 3 or _F16_ONE[0])
     args = (_p(x.buf), x.ctot, x.coff, cin, _p(x.scale), _p(x.shift), float(x.slope), _p(dy.buf), dy.ctot, dy.coff,
             cout, _p(_chk(dw, name="dw")), int(accumulate), _p(scratch)) + ((_p(dy.amax),) if f16 else ()) + (x.n, x.h, x.w, _stream())
     fn = "san_conv2d_wgrad_bf16x3_amax" if f16 else "san_conv2d_wgrad_bf16x3"
@@ -1677,7 +1698,7 @@ def _conv2d_wgrad1x1_bf16x3(x: Act, dy: Act, dw: torch.Tensor, accumulate: bool 
     nbytes = lib().query("san_conv1x1_wgrad_bf16x3_scratch_bytes", x.n, x.h, x.w, cin, cout)
     scratch_tag, restore = _wgrad_scratch_tag(dw, scratch_tag)
     scratch = arena.scratch("wgrad_bf16x3" + scratch_tag, nbytes, x.buf.device)
-    f16 = dy.amax is not None and _CONV_NP[0] == 3
+    f16 = dy.amax is not None and (_CONV_NP[0] == 3 or _F16_ONE[0])
     args = (_p(x.buf), x.ctot, x.coff, cin, _p(x.scale), _p(x.shift), float(x.slope), _p(dy.buf), dy.ctot, dy.coff,
             cout, _p(_chk(dw, name="dw")), int(accumulate), int(transposed), _p(scratch)) + ((_p(dy.amax),) if f16 else ()) + (
             x.n, x.h, x.w, _stream())
